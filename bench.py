@@ -10,8 +10,10 @@ each rank trains on its own batch of B graphs (weak scaling) and the gradients a
 flat gradient buffer (13.2 MB fp32) per step in two buckets, the first (the conv blocks, 10.4 MB)
 all_reduced while the backward's tail runs — the data-parallel exchange of SURVEY §8e.
 
-Prints one JSON line (rank 0).  Also reports the dominant kernel's roofline (HIP events around
-its launches inside the timed region) and the oracle's CPU throughput on a bounded sample.
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times ``--steps`` steps and prints the
+line (``--dump-outputs DIR`` also writes the last timed step's outputs).  With ``--full`` it also
+reports the dominant kernel's roofline (HIP events around its launches inside the timed region), the
+oracle's CPU throughput on a bounded sample, the secondary configurations and the end-to-end loops.
 """
 from __future__ import annotations
 
@@ -46,6 +48,7 @@ PROBE_STEPS = 3            # untimed replays the dominant-kernel ranking sums ov
 C1_WARM, C1_REPS = 10, 50   # config C1 forward timing (median of 50 after 10)
 CPU_BUDGET_S = 40.0        # CPU baseline: time-boxed sample (cpu_baseline)
 SERIAL_STEPS = 3           # serialised replays after the timed region (the dominant kernel's own duration)
+DUMP_MAX_ELEMS = 7_000_000  # --dump-outputs: elements per array (two large arrays: 56 MB of float32)
 
 
 def parse():
@@ -62,8 +65,16 @@ def parse():
     p.add_argument("--dry-run", action="store_true",
                    help="no GPU: every rank runs only the data-parallel exchange (gloo all_reduce of a flat "
                         "gradient of the model's size) — a CPU rehearsal of the rank plumbing")
-    p.add_argument("--steps", type=int, default=20)
-    p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--steps", type=int, default=20, help="timed steps")
+    p.add_argument("--warmup", type=int, default=5, help="untimed steps before them")
+    p.add_argument("--full", action="store_true",
+                   help="also measure everything beside the headline figure: the dominant kernel's roofline, the "
+                        "CPU baseline, the secondary configurations and the end-to-end loops (minutes).  Without "
+                        "it a run sets up, warms up, times --steps steps and prints the result line")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write what the last timed step returned and updated (the loss, the "
+                        "flat parameters, the flat gradient and its norm) as DIR/<name>.npy (float32); the inputs "
+                        "are seeded, so two builds run with the same arguments can be compared array for array")
     p.add_argument("--batch", type=int, default=32, help="graphs per GPU (BASELINE config 2: 32)")
     p.add_argument("--hidden", type=int, default=256)
     p.add_argument("--layers", type=int, default=4)
@@ -86,9 +97,9 @@ def parse():
     p.add_argument("--precision", default="fp32", choices=["fp32", "bf16"],
                    help="GEMM arithmetic: fp32 (BASELINE config 2, the default) or bf16 matrix-core inputs with "
                         "fp32 accumulation (config 3's autocast precision; a secondary line, never the fp32 number)")
-    p.add_argument("--e2e", type=int, default=10000, metavar="GRAPHS",
-                   help="also time the end-to-end loop over an HBM-resident dataset of this many graphs per rank "
-                        "(config C5's ~10k graphs; 0 = off): device collate of a random batch + CSR/compaction + "
+    p.add_argument("--e2e", type=int, default=None, metavar="GRAPHS",
+                   help="with --full: also time the end-to-end loop over an HBM-resident dataset of this many graphs "
+                        "per rank (default 10000, config C5's ~10k graphs; 0 = off): device collate of a random batch + CSR/compaction + "
                         "step, at the headline config and (one GPU) at config C5's B=256 bf16 (SURVEY §8d's "
                         "'including collate' number; separate fields, never value)")
     p.add_argument("--launch", choices=["eager", "plan", "graph"], default="plan",
@@ -106,7 +117,22 @@ def parse():
                    help="engine option of this run's model (engine.<attr>=0/1|N), trainer optimizer (optimizer=hip) "
                         "or stream priorities (loader_priority / main_priority / loader_dedicated); repeatable — for measuring "
                         "opt-in paths")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.full:
+        if args.e2e is None:
+            args.e2e = 10000
+    else:
+        # a plain run measures the headline figure only; asking for one of the other measurements
+        # without --full is an error, not a silent no-op
+        if args.e2e:
+            p.error("--e2e GRAPHS needs --full")
+        if args.dump_probes:
+            p.error("--dump-probes needs --full (the probes belong to the roofline measurement)")
+        args.e2e = 0
+        args.no_roofline = args.no_cpu_baseline = args.no_secondary = True
+    if args.dump_outputs and (args.ensemble > 0 or args.dry_run):
+        p.error("--dump-outputs writes the training step's outputs: not with --ensemble or --dry-run")
+    return args
 
 
 def apply_settings(args, model):
@@ -517,7 +543,30 @@ def _roofline(summ, dominant, mfma_peak, probe_src):
             "bytes_per_launch": s["bytes_per_launch"], "timing": probe_src}
 
 
-def measure(args, dev, rank, world, B, lg_offset, precision, steps, warmup, roofline=True, streams_of=None):
+def step_outputs(trainer):
+    """What a caller of ``trainer.step`` holds after it: the returned loss and the state the step
+    updated (flat parameters, flat gradient, the gradient norm the clip used), as device copies."""
+    out = {"loss": trainer.loss, "params": trainer.st.flat, "grad": trainer.st.grad}
+    if trainer.optimizer == "hip":
+        out["grad_norm"] = trainer.gnorm
+    return {k: v.detach().clone() for k, v in out.items()}
+
+
+def dump_outputs(path, outputs):
+    """DIR/<name>.npy, float32 (the headline model: 3.3 M parameters, 26 MB in all).  An array of
+    more than DUMP_MAX_ELEMS elements (a much larger --hidden / --layers) is written as a fixed,
+    seeded sample of that many, so that the files stay under 64 MB together."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in outputs.items():
+        a = t.float().cpu().numpy().astype(np.float32, copy=False).reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, size=DUMP_MAX_ELEMS, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def measure(args, dev, rank, world, B, lg_offset, precision, steps, warmup, roofline=True, streams_of=None,
+            keep_outputs=False):
     """Builds the model, trainer and a resident batch of B graphs, picks the dominant kernel (one
     untimed eager probe step), captures the step, runs `warmup` steps and times exactly `steps`
     (barrier + synchronize on both sides, max over ranks).  Returns the numbers and the trainer.
@@ -622,6 +671,8 @@ def measure(args, dev, rank, world, B, lg_offset, precision, steps, warmup, roof
         dist.barrier()
     dt = time.perf_counter() - t0
     profiling.disable()
+    # the last timed step's outputs, copied before any later replay (roofline) steps the model on
+    outputs = step_outputs(trainer) if keep_outputs else None
     if world > 1:
         dt = max_over_ranks(dt, dev)
     if probe_in_graph:
@@ -673,7 +724,7 @@ def measure(args, dev, rank, world, B, lg_offset, precision, steps, warmup, roof
         "survey_hbm_frac": round(survey_bytes_per_graph(2 if precision == "bf16" else 4) / 1e9 * value / world
                                  / HBM_PEAK_GBS, 4)}
     return {"value": value, "dt": dt, "ms_per_step": dt / steps * 1e3, "launch": launch_mode, "roofline": roof,
-            "step_roofline": step_roof, "trainer": trainer, "batch": batch}
+            "step_roofline": step_roof, "trainer": trainer, "batch": batch, "outputs": outputs}
 
 
 def ensemble_bench(args, dev, rank, world):
@@ -875,7 +926,11 @@ def main():
     if args.e2e > 0 and "store_first" in sec_on:   # diagnostics: the dataset resident before any step
         store, t_build = build_store(args, dev, rank)
     r = measure(args, dev, rank, world, B, args.lg_offset, args.precision, args.steps, args.warmup,
-                roofline=not args.no_roofline)
+                roofline=not args.no_roofline, keep_outputs=bool(args.dump_outputs) and rank == 0)
+    outputs = r.pop("outputs")
+    if outputs is not None:
+        dump_outputs(args.dump_outputs, outputs)
+        del outputs
 
     # secondary lines of the default run (one GPU): the same step with the corrected line-graph
     # wiring (SURVEY §8d "also report num_edges": no compaction, every bond active) and config C3

@@ -40,6 +40,30 @@ def test_world_size_mismatch_is_refused():
     assert r.returncode != 0 and "WORLD_SIZE=1" in (r.stderr + r.stdout)
 
 
+def test_plain_run_measures_the_headline_only_and_full_restores_the_rest(monkeypatch):
+    """Without --full every measurement beside the timed steps is off, and asking for one of them is an
+    error; --full keeps the earlier defaults (and its own --no-* switches)."""
+    import pytest
+    sys.path.insert(0, REPO)
+    import bench
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        return bench.parse()
+
+    a = parse("--gpus", "1", "--steps", "7", "--warmup", "3")
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, "")
+    assert a.e2e == 0 and a.no_roofline and a.no_cpu_baseline and a.no_secondary
+    assert parse("--e2e", "0", "--no-secondary").e2e == 0        # the earlier "off" switches stay accepted
+    for bad in (["--e2e", "100"], ["--dump-probes", "p.json"], ["--dump-outputs", "d", "--ensemble", "2"]):
+        with pytest.raises(SystemExit):
+            parse(*bad)
+    f = parse("--full")
+    assert f.e2e == 10000 and not (f.no_roofline or f.no_cpu_baseline or f.no_secondary)
+    f = parse("--full", "--e2e", "300", "--no-roofline", "--dump-outputs", "d")
+    assert f.e2e == 300 and f.no_roofline and not f.no_secondary and f.dump_outputs == "d"
+
+
 def test_launcher_counts_gpus_without_touching_hip():
     """The self-launch path counts devices in a child interpreter: the launching process itself never
     initialises HIP (a process that did must not start another program on this pool)."""

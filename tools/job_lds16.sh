@@ -31,5 +31,5 @@ else                         # second pass: the default rule (A k-contiguous) ag
   done
   run suite 600 "${PT[@]}" tests
   run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-  run bench 600 python bench.py
+  run bench 600 python bench.py --full
 fi

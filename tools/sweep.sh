@@ -3,6 +3,7 @@
 # "-" = defaults).  Stops at the first crash/timeout.  Usage: tools/sweep.sh "-" "engine.skinny_encoder=1" ...
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
 mkdir -p gpurun_out
+EXTRA_BENCH_ARGS="--full ${EXTRA_BENCH_ARGS}"   # the roofline columns and the e2e loop are --full measurements
 for cfg in "$@"; do
   sets=()
   if [ "$cfg" != "-" ]; then for s in $cfg; do sets+=(--set "$s"); done; fi
