@@ -1280,11 +1280,14 @@ def readout_feats_fwd(h, ptr, global_x, gdim, sg, sgdim, feats, drop_p, seed):
 
 
 def readout_pool_bwd(dfeats, ptr, batch, dh, accumulate, drop_p, seed):
+    """dfeats [B, W]: the gradient of readout_feats_fwd's feats (any row stride; the first D columns
+    are read).  Its width W = D + gdim + sgdim indexes the dropout mask, as in the forward."""
     B = ptr.numel() - 1
     N, D = dh.shape
-    check(_lib.lib().alignn_readout_pool_bwd(B, N, D, dfeats.data_ptr(), dfeats.stride(0), ptr.data_ptr(),
-                                             batch.data_ptr(), dh.data_ptr(), int(accumulate), float(drop_p),
-                                             int(seed) & (2**64 - 1), stream_ptr()), "alignn_readout_pool_bwd")
+    check(_lib.lib().alignn_readout_pool_bwd_w(B, N, D, dfeats.data_ptr(), dfeats.stride(0), dfeats.size(1),
+                                               ptr.data_ptr(), batch.data_ptr(), dh.data_ptr(), int(accumulate),
+                                               float(drop_p), int(seed) & (2**64 - 1), stream_ptr()),
+          "alignn_readout_pool_bwd_w")
 
 
 def dropout(x, y, relu_ref=None, drop_p=0.0, seed=0):

@@ -389,7 +389,9 @@ __global__ void readout_fwd_kernel(int64_t B, int D, const float* __restrict__ h
   }
 }
 
-__global__ void pool_bwd_kernel(int64_t N, int D, const float* __restrict__ dfeats, int64_t ldf,
+// W: the forward's feats width D + gdim + sgdim — the mask of element (b, c) is drawn under index
+// b * W + c, as readout_fwd_kernel drew it, whatever the row stride ldf of dfeats.
+__global__ void pool_bwd_kernel(int64_t N, int D, const float* __restrict__ dfeats, int64_t ldf, int64_t W,
                                 const int64_t* __restrict__ ptr, const int64_t* __restrict__ batch,
                                 float* __restrict__ dh, int acc, DropParams drop) {
   resolve_drop(drop);
@@ -401,7 +403,7 @@ __global__ void pool_bwd_kernel(int64_t N, int D, const float* __restrict__ dfea
     const float cnt = (float)max((int64_t)1, ptr[b + 1] - ptr[b]);
     for (int c = lane; c < D; c += 64) {
       float v = dfeats[b * ldf + c] / cnt;
-      if (drop.active) v *= dropout_mul(drop.seed, (uint64_t)b * ldf + c, drop.thresh, drop.inv_keep);
+      if (drop.active) v *= dropout_mul(drop.seed, (uint64_t)b * W + c, drop.thresh, drop.inv_keep);
       const int64_t i = node * D + c;
       dh[i] = acc ? dh[i] + v : v;
     }
@@ -757,16 +759,27 @@ extern "C" int alignn_readout_feats_fwd(int64_t B, int32_t D, const float* h, co
   return ALIGNN_OK;
 }
 
-extern "C" int alignn_readout_pool_bwd(int64_t B, int64_t N, int32_t D, const float* dfeats, int64_t ldf,
-                                       const int64_t* ptr, const int64_t* batch, float* dh, int32_t accumulate,
-                                       float drop_p, uint64_t seed, void* stream) {
+extern "C" int alignn_readout_pool_bwd_w(int64_t B, int64_t N, int32_t D, const float* dfeats, int64_t ldf,
+                                         int64_t W, const int64_t* ptr, const int64_t* batch, float* dh,
+                                         int32_t accumulate, float drop_p, uint64_t seed, void* stream) {
   (void)B;
+  if (W < D || ldf < D) {
+    set_error("readout_pool_bwd: feats width %lld / dfeats stride %lld below hidden %d", (long long)W, (long long)ldf,
+              D);
+    return ALIGNN_E_BAD_SHAPE;
+  }
   if (N == 0) return ALIGNN_OK;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  launch(pool_bwd_kernel, dim3(grid_for(N, 4)), dim3(256), 0, s, N, D, dfeats, ldf, ptr, batch, dh,
+  launch(pool_bwd_kernel, dim3(grid_for(N, 4)), dim3(256), 0, s, N, D, dfeats, ldf, W, ptr, batch, dh,
                      accumulate, make_drop(drop_p, seed));
   ALIGNN_LAUNCH_CHECK("pool_bwd_kernel");
   return ALIGNN_OK;
+}
+
+extern "C" int alignn_readout_pool_bwd(int64_t B, int64_t N, int32_t D, const float* dfeats, int64_t ldf,
+                                       const int64_t* ptr, const int64_t* batch, float* dh, int32_t accumulate,
+                                       float drop_p, uint64_t seed, void* stream) {
+  return alignn_readout_pool_bwd_w(B, N, D, dfeats, ldf, ldf, ptr, batch, dh, accumulate, drop_p, seed, stream);
 }
 
 extern "C" int alignn_dropout_f32(int64_t rows, int64_t cols, const float* x, int64_t ldx, float* y, int64_t ldy,

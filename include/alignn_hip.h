@@ -486,6 +486,9 @@ int alignn_gate_ln_bwd_partials_ex(int64_t n, int32_t D, float* dXnew, int64_t l
  * Readout (train.py:562-586): global_mean_pool over ptr (PyG, train.py:562), concat with
  * global_x / sg_one_hot (train.py:563-572), dropout (train.py:573).
  * feats [B, D + G]  (G = gdim + sgdim).  Backward scatters dpooled/count to the atoms.
+ * The dropout mask of feats element (b, c) is drawn under index b * (D + G) + c.  The backward
+ * reads the first D columns of dfeats [B, ldf]; alignn_readout_pool_bwd_w takes the forward's width
+ * W = D + G for the mask index, alignn_readout_pool_bwd assumes W = ldf (dfeats laid out like feats).
  * ---------------------------------------------------------------------------------------- */
 int alignn_readout_feats_fwd(int64_t B, int32_t D, const float* h, const int64_t* ptr,
                              const float* global_x, int32_t gdim, const float* sg, int32_t sgdim,
@@ -493,6 +496,9 @@ int alignn_readout_feats_fwd(int64_t B, int32_t D, const float* h, const int64_t
 int alignn_readout_pool_bwd(int64_t B, int64_t N, int32_t D, const float* dfeats, int64_t ldf,
                             const int64_t* ptr, const int64_t* batch, float* dh, int32_t accumulate,
                             float drop_p, uint64_t seed, void* stream);
+int alignn_readout_pool_bwd_w(int64_t B, int64_t N, int32_t D, const float* dfeats, int64_t ldf, int64_t W,
+                              const int64_t* ptr, const int64_t* batch, float* dh, int32_t accumulate,
+                              float drop_p, uint64_t seed, void* stream);
 
 /* Elementwise dropout (+ optional ReLU-mask backward): y = x * keep/(1-p) [* (ref > 0)] */
 int alignn_dropout_f32(int64_t rows, int64_t cols, const float* x, int64_t ldx, float* y, int64_t ldy,

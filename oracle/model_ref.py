@@ -36,24 +36,31 @@ def _mlp2(x, st, prefix):
     return F.linear(h, st[prefix + "2.weight"], st[prefix + "2.bias"])
 
 
-def edge_block(st, prefix, edge_state, lg_edge_index, angle_emb, heads, dropout=0.0, training=False):
-    """train.py:312-317"""
+def edge_block(st, prefix, edge_state, lg_edge_index, angle_emb, heads, dropout=0.0, training=False,
+               dropout_fn=None, site=0):
+    """train.py:312-317.  ``dropout_fn`` (tests): the two dropouts become ``dropout_fn(site, alpha)``
+    (attention) and ``dropout_fn(site + 1, relu(LN(.)))`` instead of ``F.dropout``."""
     if edge_state.numel() == 0 or angle_emb.numel() == 0 or lg_edge_index.numel() == 0:
         return edge_state
     out = transformer_conv(edge_state, lg_edge_index, angle_emb, _sub(st, prefix + "conv."), heads,
-                           dropout=dropout, training=training)
+                           dropout=dropout, training=training, dropout_fn=dropout_fn, site=site)
     out = F.layer_norm(out, (out.size(-1),), st[prefix + "norm.weight"], st[prefix + "norm.bias"], 1e-5)
+    if dropout_fn is not None:
+        return edge_state + dropout_fn(site + 1, F.relu(out))
     return edge_state + F.dropout(F.relu(out), p=dropout, training=training)
 
 
-def node_block(st, prefix, node_state, edge_index, edge_state, heads, dropout=0.0, training=False):
-    """train.py:330-336"""
+def node_block(st, prefix, node_state, edge_index, edge_state, heads, dropout=0.0, training=False,
+               dropout_fn=None, site=0):
+    """train.py:330-336.  ``dropout_fn``, ``site``: as in :func:`edge_block`."""
     if edge_state.numel() == 0 or edge_index.numel() == 0:
         return node_state
     edge_attr = F.linear(edge_state, st[prefix + "edge_proj.weight"], st[prefix + "edge_proj.bias"])
     out = transformer_conv(node_state, edge_index, edge_attr, _sub(st, prefix + "conv."), heads,
-                           dropout=dropout, training=training)
+                           dropout=dropout, training=training, dropout_fn=dropout_fn, site=site)
     out = F.layer_norm(out, (out.size(-1),), st[prefix + "norm.weight"], st[prefix + "norm.bias"], 1e-5)
+    if dropout_fn is not None:
+        return node_state + dropout_fn(site + 1, F.relu(out))
     return node_state + F.dropout(F.relu(out), p=dropout, training=training)
 
 
@@ -64,8 +71,14 @@ def num_layers(st: Dict[str, torch.Tensor]) -> int:
     return l
 
 
-def hetero_forward(st, data, heads, dropout=0.0, training=False, return_shared=False, retain=None):
-    """``HeteroAlignnRegressor.forward`` (train.py:537-586).  Returns (mean [B,T], logvar [B,T])."""
+def hetero_forward(st, data, heads, dropout=0.0, training=False, return_shared=False, retain=None,
+                   dropout_fn=None):
+    """``HeteroAlignnRegressor.forward`` (train.py:537-586).  Returns (mean [B,T], logvar [B,T]).
+
+    ``dropout_fn`` (tests): when given, every dropout is ``dropout_fn(site, tensor)`` instead of
+    ``F.dropout``, with the engine's site numbers (dropout sites): 4l / 4l+1 the line
+    block l's attention / gate, 4l+2 / 4l+3 the atom block's, 4L the readout feats, 4L+1 the shared
+    layer."""
     hidden = st["base.node_encoder.2.weight"].size(0)
     node_state = _mlp2(data.x, st, "base.node_encoder.")
     if data.edge_attr.numel() > 0:
@@ -82,12 +95,12 @@ def hetero_forward(st, data, heads, dropout=0.0, training=False, return_shared=F
         retain["e0"] = edge_state
     for l in range(num_layers(st)):
         edge_state = edge_block(st, f"base.edge_blocks.{l}.", edge_state, data.lg_edge_index, angle_emb,
-                                heads, dropout, training)
+                                heads, dropout, training, dropout_fn, 4 * l)
         if retain is not None:
             edge_state.retain_grad()
             retain[f"e{l + 1}"] = edge_state
         node_state = node_block(st, f"base.node_blocks.{l}.", node_state, data.edge_index, edge_state,
-                                heads, dropout, training)
+                                heads, dropout, training, dropout_fn, 4 * l + 2)
         if retain is not None:
             node_state.retain_grad()
             retain[f"h{l + 1}"] = node_state
@@ -101,9 +114,16 @@ def hetero_forward(st, data, heads, dropout=0.0, training=False, return_shared=F
         sg = sg.unsqueeze(0)
     sg = sg.reshape(pooled.size(0), -1)
     feats = torch.cat([pooled, torch.cat([global_x, sg], dim=1)], dim=1)
-    feats = F.dropout(feats, p=dropout, training=training)
+    L = num_layers(st)
+    if dropout_fn is None:
+        feats = F.dropout(feats, p=dropout, training=training)
+    else:
+        feats = dropout_fn(4 * L, feats)
     shared = F.relu(F.linear(feats, st["base.feat_proj.0.weight"], st["base.feat_proj.0.bias"]))
-    shared = F.dropout(shared, p=dropout, training=training)
+    if dropout_fn is None:
+        shared = F.dropout(shared, p=dropout, training=training)
+    else:
+        shared = dropout_fn(4 * L + 1, shared)
     if return_shared:
         return shared
     t = 0

@@ -57,12 +57,17 @@ def transformer_conv(
     dropout: float = 0.0,
     training: bool = False,
     return_alpha: bool = False,
+    dropout_fn=None,
+    site: int = 0,
 ):
     """Functional restatement of PyG 2.7.0 ``TransformerConv.forward``.
 
     ``p`` holds the module's parameters under their state-dict names
     (``lin_query.weight``, ``lin_key.bias``, ``lin_edge.weight``, ``lin_beta.weight``, ...).
     Flow is ``source_to_target``: j = edge_index[0] (source), i = edge_index[1] (target).
+
+    ``dropout_fn`` (tests): when given, the attention dropout is ``dropout_fn(site, alpha)`` — a
+    caller-supplied mask on alpha [m, H] in edge order — instead of ``F.dropout``.
     """
     n = x.size(0)
     D_out = p["lin_query.weight"].size(0)
@@ -82,7 +87,10 @@ def transformer_conv(
     alpha = (query_i * key_j).sum(dim=-1) / math.sqrt(C)
     alpha = segment_softmax(alpha, dst, n)
     alpha_saved = alpha
-    alpha = F.dropout(alpha, p=dropout, training=training)
+    if dropout_fn is None:
+        alpha = F.dropout(alpha, p=dropout, training=training)
+    else:
+        alpha = dropout_fn(site, alpha)
     msg = (value_j + e) * alpha.view(-1, H, 1)
     # aggregate (aggr='add')
     out = scatter_sum(msg, dst, n).view(-1, H * C)

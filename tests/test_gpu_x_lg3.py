@@ -92,10 +92,13 @@ def test_xcd_item_order_bitwise(drop):
         assert torch.equal(a[k], b[k]), k
 
 
-def _pyg_reference(csr_cpu_ei, n, t, H, D=256):
+def _pyg_reference(csr_cpu_ei, n, t, H, D=256, mask=None, p=0.0):
     """Float64 PyG TransformerConv attention on the engine's operands: with
     M_h the per-head edge map, z = <Q_d, K_s + M_h f_t + w̄_h>/sqrt(C) is written as
-    <Q_dh, K_sh>/sqrt(C) + (<u_dh, f_t> + <w̄_h, Q_dh>)/sqrt(C) (u = M_h^T Q_dh given as U)."""
+    <Q_dh, K_sh>/sqrt(C) + (<u_dh, f_t> + <w̄_h, Q_dh>)/sqrt(C) (u = M_h^T Q_dh given as U).
+    mask (bool [m, H] by edge position) and p: attention dropout, alpha' = alpha * mask / (1 - p) in
+    outp, S, sumA and in the target-side backward (dq, Sz, sigz, dz, al: the contract of
+    alignn_tconv_bwd_dst on Vd / dout, al = alpha'); ``alpha`` stays the softmax itself."""
     C = D // H
     src, dst = csr_cpu_ei
     QKV = t["QKVR"].double().cpu()
@@ -111,10 +114,21 @@ def _pyg_reference(csr_cpu_ei, n, t, H, D=256):
     ex = torch.exp(z - zmax[dst])
     den = torch.zeros(n, H, dtype=torch.float64).index_add(0, dst, ex) + 1e-16
     alpha = ex / den[dst]
-    aggV = torch.zeros(n, H, C, dtype=torch.float64).index_add(0, dst, alpha[:, :, None] * V[src])
-    S = torch.zeros(n, H, D, dtype=torch.float64).index_add(0, dst, alpha[:, :, None] * Fe[:, None, :])
-    return dict(outp=aggV.reshape(n, D), S=S, sumA=torch.zeros(n, H, dtype=torch.float64).index_add(0, dst, alpha),
-                alpha=alpha)
+    keep = torch.ones(m, H, dtype=torch.float64) if mask is None else mask.double() / (1.0 - p)
+    al = alpha * keep
+    aggV = torch.zeros(n, H, C, dtype=torch.float64).index_add(0, dst, al[:, :, None] * V[src])
+    S = torch.zeros(n, H, D, dtype=torch.float64).index_add(0, dst, al[:, :, None] * Fe[:, None, :])
+    out = dict(outp=aggV.reshape(n, D), S=S, sumA=torch.zeros(n, H, dtype=torch.float64).index_add(0, dst, al),
+               alpha=alpha)
+    # target-side backward (the kernels' contract, as tests/test_gpu_x_pending.py::_attention_ref)
+    Vd, dout = t["Vd"].double().cpu(), t["dout"].double().cpu().view(n, H, C)
+    g = (dout[dst] * V[src]).sum(-1) + (Vd[dst] * Fe[:, None, :]).sum(-1) + (dout[dst] * wb).sum(-1)
+    pdl = (dout * aggV).sum(-1)
+    dz = alpha * (g * keep - pdl[dst]) / C ** 0.5
+    out.update(dq=torch.zeros(n, H, C, dtype=torch.float64).index_add(0, dst, dz[:, :, None] * K[src]).reshape(n, D),
+               Sz=torch.zeros(n, H, D, dtype=torch.float64).index_add(0, dst, dz[:, :, None] * Fe[:, None, :]),
+               sigz=torch.zeros(n, H, dtype=torch.float64).index_add(0, dst, dz), dz=dz, al=al)
+    return out
 
 
 @pytest.mark.parametrize("H", [1, 4])
@@ -127,3 +141,23 @@ def test_wave_items_forward_vs_float64_pyg(H):
     assert _rel(b["outp"].cpu(), ref["outp"]) < 1e-5
     assert _rel(b["S"].cpu(), ref["S"]) < 1e-5
     assert _rel(b["sumA"].cpu(), ref["sumA"]) < 1e-5
+
+
+@pytest.mark.parametrize("H", [1, 4])
+def test_wave_items_dropout_vs_float64_pyg(H):
+    """Forward and target-side backward at dropout 0.15 against PyG's attention in float64 with the
+    kernels' keep mask reproduced on the host (tests/_dropout_ref.py: element t * H + h of the call's
+    seed): the mask scales alpha in outp, S and sumA alike and the backward re-draws the same one."""
+    import _dropout_ref as dr
+    _ops().set_step_seed(None)
+    p = 0.15
+    degs = DEGREES["ragged"]
+    csr, m, t = _case(H, degs, 7, True)
+    fam, b = _run(csr, m, t, 256, H, p, True)
+    assert fam == 3
+    mask = torch.from_numpy(dr.keep_mask(77, m * H, p).reshape(m, H))   # _run's seed
+    assert 0.10 < float((~mask).double().mean()) < 0.20
+    ref = _pyg_reference((t["src"], t["dst"]), len(degs), t, H, mask=mask, p=p)
+    assert torch.equal(b["al"].cpu() == 0, ~mask)
+    for k in ("outp", "S", "sumA", "dq", "Sz", "sigz", "dz", "al"):
+        assert _rel(b[k].cpu(), ref[k]) < 1e-5, (k, H)

@@ -212,10 +212,13 @@ def _run_tconv(csr, m, t, D, H, drop, heavy_threshold):
                 dF=dF)
 
 
-def _attention_ref(csr, m, t, D, H):
+def _attention_ref(csr, m, t, D, H, mask=None, p=0.0):
     """fp64 restatement of the kernels' contract (include/alignn_hip.h, alignn_tconv_fwd/_bwd_dst;
-    PyG TransformerConv.message + softmax(+1e-16) with the edge-feature algebra of DESIGN.md §3),
-    no dropout.  Edge position t: target-sorted (csr.src_at / dst_at); F row feat_row[t] or t."""
+    PyG TransformerConv.message + softmax(+1e-16) with the edge-feature algebra of DESIGN.md §3).
+    Edge position t: target-sorted (csr.src_at / dst_at); F row feat_row[t] or t.
+    mask (bool [m, H], by edge position) and p: attention dropout, alpha' = alpha * mask / (1 - p) in
+    outp, S, sumA and the backward (dL/dalpha = mask / (1 - p) * dL/dalpha'); the ``al`` the kernels
+    write per edge is alpha'.  None: no dropout."""
     import math
     n, C = csr.n, D // H
     d64 = lambda x: x.detach().double().cpu()  # noqa: E731
@@ -232,13 +235,15 @@ def _attention_ref(csr, m, t, D, H):
         0, dst[:, None].expand(m, H), z, "amax", include_self=True)
     ex = torch.exp(z - mst[dst])
     den = z64(n, H).index_add_(0, dst, ex) + 1e-16
-    al = ex / den[dst]
+    alpha = ex / den[dst]
+    keep = torch.ones(m, H, dtype=torch.float64) if mask is None else mask.double() / (1.0 - p)
+    al = alpha * keep
     outp = z64(n, H, C).index_add_(0, dst, al[..., None] * V[src]).view(n, D)
     S = z64(n, H, D).index_add_(0, dst, al[..., None] * F[:, None, :])
     sumA = z64(n, H).index_add_(0, dst, al)
     g = (dout[dst] * V[src]).sum(-1) + torch.einsum("mhd,md->mh", Vd[dst], F) + (dout[dst] * wb).sum(-1)
     pdl = (dout * outp.view(n, H, C)).sum(-1)
-    dz = al * (g - pdl[dst]) / math.sqrt(C)
+    dz = alpha * (g * keep - pdl[dst]) / math.sqrt(C)
     dq = z64(n, H, C).index_add_(0, dst, dz[..., None] * K[src]).view(n, D)
     Sz = z64(n, H, D).index_add_(0, dst, dz[..., None] * F[:, None, :])
     sigz = z64(n, H).index_add_(0, dst, dz)
@@ -261,6 +266,26 @@ def test_light_heavy_attention_kernels_vs_fp64(D, H, thr):
         ref = _attention_ref(csr, m, t, D, H)
         for k in ref:
             assert _rel(got[k].cpu(), ref[k]) < 2e-5, (k, D, H, thr, seed)
+
+
+@pytest.mark.parametrize("D,H", [(256, 4), (64, 1)])
+def test_light_heavy_attention_dropout_vs_fp64(D, H):
+    """The same kernels at dropout 0.15 (thr 32: both the 4-wave and the 1-wave path) against the
+    fp64 restatement with the kernels' keep mask reproduced on the host (tests/_dropout_ref.py:
+    element t * H + h of the call's seed, t the target-sorted edge position): the mask reaches outp,
+    S and sumA alike, and the backward re-draws it under the same index."""
+    import _dropout_ref as dr
+    _ops().set_step_seed(None)
+    p = 0.15
+    for seed, (with_wbar, feat_row) in enumerate([(True, False), (False, True)]):
+        csr, m, t = _tconv_case(D, H, 300, 70, 10 + seed, with_wbar, feat_row)
+        got = _run_tconv(csr, m, t, D, H, p, 32)
+        mask = torch.from_numpy(dr.keep_mask(77, m * H, p).reshape(m, H))   # _run_tconv's seed
+        assert 0.10 < float((~mask).double().mean()) < 0.20
+        ref = _attention_ref(csr, m, t, D, H, mask=mask, p=p)
+        assert torch.equal(got["al"].cpu() == 0, ~mask)
+        for k in ref:
+            assert _rel(got[k].cpu(), ref[k]) < 2e-5, (k, D, H, seed)
 
 
 @pytest.mark.parametrize("D,H", [(256, 4), (128, 2)])
