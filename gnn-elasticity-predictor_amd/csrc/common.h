@@ -98,6 +98,25 @@ __device__ __forceinline__ float group_sum(float v, int width) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// Activations and clamps as torch computes them on non-finite values ("Non-finite
+// values").  fmaxf / fminf return the other operand when one is NaN, so a bare fmaxf(v, 0.f)
+// turns a NaN into 0; torch.relu, torch.clamp and clip_grad_norm_ keep it.  clamp_min(v, lo) is
+// v != v ? v : fmaxf(v, lo), written as IEEE 754-2019 maximum: one v_maximum3_f32 on gfx950 (the
+// bare fmaxf is two v_max_f32, the select form four instructions).  Finite results, +-inf and the
+// sign of zero (max(-0, +0) = +0 either way) are bitwise those of the bare fmaxf / fminf.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ float clamp_min(float v, float lo) { return __builtin_elementwise_maximum(v, lo); }
+__device__ __forceinline__ float clamp_max(float v, float hi) { return __builtin_elementwise_minimum(v, hi); }
+__device__ __forceinline__ float relu_f(float v) { return clamp_min(v, 0.f); }
+// ReLU backward from the forward result (torch threshold_backward: result <= 0 ? 0 : grad): a NaN
+// result passes the gradient.
+__device__ __forceinline__ bool relu_on(float result) { return !(result <= 0.f); }
+__device__ __forceinline__ float relu_bwd(float result, float g) { return relu_on(result) ? g : 0.f; }
+// ReLU on rounded bf16 values (autocast's order: the Linear's bf16 output, then ReLU): zero and
+// every negative number become +0, a NaN of either sign keeps its bits.
+__device__ __forceinline__ __bf16 relu_bf(__bf16 b) { return ((float)b <= 0.f) ? (__bf16)0.f : b; }
+
+// ---------------------------------------------------------------------------------------------
 // Counter-based random numbers (dropout masks / jitter).  Each call site gets its own 64-bit
 // seed from the host; the element counter makes the mask reproducible in the backward pass.
 // ---------------------------------------------------------------------------------------------

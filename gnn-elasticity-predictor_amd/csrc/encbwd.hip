@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void enc_bwd_kernel(EncBwdParams p) {
           float pre = 0.f;
 #pragma unroll
           for (int k = 0; k < KM; ++k) pre = fmaf(r[2 * EB_HL + k], w[k], pre);
-          const float dp = (pre + bj) > 0.f ? g : 0.f;
+          const float dp = relu_bwd(pre + bj, g);
           accb += dp;
 #pragma unroll
           for (int k = 0; k < KM; ++k) acc[k] = fmaf(dp, r[2 * EB_HL + k], acc[k]);
@@ -376,13 +376,13 @@ void enc_bwd_bf16_kernel(EncBwdParams p, const uint16_t* __restrict__ F16, int64
         if constexpr (XF) {
           const ebx16 pre = __builtin_amdgcn_mfma_f32_32x32x16_bf16(XA, W1B[ct], ebx16{}, 0, 0, 0);
 #pragma unroll
-          for (int i = 0; i < 16; ++i) GA[i >> 3][i & 7] = (__bf16)((float)(__bf16)pre[i] > 0.f ? G[i] : 0.f);
+          for (int i = 0; i < 16; ++i) GA[i >> 3][i & 7] = (__bf16)relu_bwd((float)(__bf16)pre[i], G[i]);
         } else {
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const int e = (i & 3) + 8 * (i >> 2) + 4 * hh;
             const uint32_t fb = fs[e * EBF_FP + col];
-            GA[i >> 3][i & 7] = (__bf16)(__builtin_bit_cast(float, fb << 16) > 0.f ? G[i] : 0.f);
+            GA[i >> 3][i & 7] = (__bf16)relu_bwd(__builtin_bit_cast(float, fb << 16), G[i]);
           }
         }
         Z[ct] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(GA[0], XB[0], Z[ct], 0, 0, 0);

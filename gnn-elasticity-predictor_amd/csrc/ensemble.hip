@@ -25,7 +25,7 @@ __global__ void ensemble_moments_kernel(int M, int64_t B, int T, const float* __
   for (int j = 0; j < M; ++j) {
     const float* h = heads + j * sm + b * ldh;
     const float mu = h[t];
-    const float lv = fmaxf(h[T + t], floor_lv);
+    const float lv = clamp_min(h[T + t], floor_lv);
     smu += mu;
     smu2 += mu * mu;
     svar += expf(lv);
@@ -33,7 +33,7 @@ __global__ void ensemble_moments_kernel(int M, int64_t B, int T, const float* __
   const float inv = 1.0f / (float)M;
   const float mean = smu * inv;
   const float var = svar * inv + smu2 * inv - mean * mean;
-  const float sd = sqrtf(fmaxf(var, 1e-12f));
+  const float sd = sqrtf(clamp_min(var, 1e-12f));
   if (mean_z) mean_z[i] = mean;
   if (std_z) std_z[i] = sd;
   if (log_means && log_stds) {
@@ -42,11 +42,11 @@ __global__ void ensemble_moments_kernel(int M, int64_t B, int T, const float* __
     const float ls = sd * s;
     const float mo = expf(lm);
     const float vl = (expf(ls * ls) - 1.0f) * expf(2.0f * lm + ls * ls);
-    const float sl = sqrtf(fmaxf(vl, 0.0f));
+    const float sl = sqrtf(clamp_min(vl, 0.0f));
     if (mean_orig) mean_orig[i] = mo;
     if (std_lin) std_lin[i] = sl;
     const float z90 = 1.6448536269514722f;
-    if (lo90) lo90[i] = fmaxf(mo - z90 * sl, 0.0f);
+    if (lo90) lo90[i] = clamp_min(mo - z90 * sl, 0.0f);
     if (hi90) hi90[i] = mo + z90 * sl;
   }
 }

@@ -22,6 +22,7 @@
 // kernels.  K < KT is zero-padded (the edge MLP's K = 36 runs as KT = 64).  Loads and stores are
 // unconditional: rows past M are clamped for loads and dropped by the store descriptor.
 #include "gemm_tile.h"
+#include "vec.h"
 
 namespace alignn {
 namespace rsk {
@@ -196,7 +197,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_rows_kernel(GemmParams p, int nite
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) Ls[((r & 3) + 8 * (r >> 2) + 4 * h) * EPI_LD + l32] = __fmul_rn(p.alpha, acc[r]);
-    const gf4 zero = {0.f, 0.f, 0.f, 0.f};
     auto finish = [&](gf4 v, int c, int ps) -> gf4 {   // beta, bias, ReLU, mask of four values at column c
       if constexpr (BETA)
         v = gf4{fmaf(p.beta, cv[ps].x, v.x), fmaf(p.beta, cv[ps].y, v.y), fmaf(p.beta, cv[ps].z, v.z),
@@ -205,10 +205,9 @@ __global__ __launch_bounds__(NT, 1) void gemm_rows_kernel(GemmParams p, int nite
         const gf4 bb = *reinterpret_cast<const gf4*>(Lb + c);
         v = gf4{__fadd_rn(v.x, bb.x), __fadd_rn(v.y, bb.y), __fadd_rn(v.z, bb.z), __fadd_rn(v.w, bb.w)};
       }
-      v = p.relu ? __builtin_elementwise_max(v, zero) : v;
+      v = p.relu ? relu4(v) : v;
       if constexpr (MASK) {
-        v.x = mk[ps].x > 0.f ? v.x : 0.f; v.y = mk[ps].y > 0.f ? v.y : 0.f;
-        v.z = mk[ps].z > 0.f ? v.z : 0.f; v.w = mk[ps].w > 0.f ? v.w : 0.f;
+        v = relu_bwd4(mk[ps], v);
       }
       return v;
     };
@@ -393,7 +392,6 @@ __global__ __launch_bounds__(NT, 1) void gemm_heads_kernel(GemmParams p, int64_t
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) Ls[((r & 3) + 8 * (r >> 2) + 4 * h) * EPI_LD + l32] = __fmul_rn(p.alpha, acc[r]);
-    const gf4 zero = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int ps = 0; ps < PASS; ++ps) {
       const int rr = RPP * ps + er;
@@ -410,7 +408,7 @@ __global__ __launch_bounds__(NT, 1) void gemm_heads_kernel(GemmParams p, int64_t
         const gf4 b2 = *reinterpret_cast<const gf4*>(Lb2 + cb);
         v = gf4{fmaf(rsv[ps], b2.x, v.x), fmaf(rsv[ps], b2.y, v.y), fmaf(rsv[ps], b2.z, v.z), fmaf(rsv[ps], b2.w, v.w)};
       }
-      v = p.relu ? __builtin_elementwise_max(v, zero) : v;
+      v = p.relu ? relu4(v) : v;
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), cst, (int)(((row0 + rr) * p.scm + ec) * 4), 0, 0);
     }
     if (b1 >= nbands) break;

@@ -272,8 +272,8 @@ __device__ __forceinline__ float epilogue_value(const GemmParams& p, int64_t b, 
   if (p.beta != 0.f) v = fmaf(p.beta, Cb[c_row(p, row) * p.scm + col * p.scn], v);
   if (p.bias) v = __fadd_rn(v, p.bias[b * p.sbias_b + col]);
   if (p.rowscale) v = fmaf(p.rowscale[b * p.srs_b + row * p.srs_m], p.bias2[b * p.sb2_b + col], v);
-  if (p.relu) v = fmaxf(v, 0.f);
-  if (p.mask) v = p.mask[row * p.smk_m + col * p.smk_n] > 0.f ? v : 0.f;
+  if (p.relu) v = relu_f(v);
+  if (p.mask) v = relu_bwd(p.mask[row * p.smk_m + col * p.smk_n], v);
   return v;
 }
 
@@ -409,8 +409,8 @@ __device__ __forceinline__ void store_tile(const GemmParams& p, const floatx16 (
           if (p.beta != 0.f) x = fmaf(p.beta, cv[u], x);
           if (p.bias) x = __fadd_rn(x, bv);
           if (p.rowscale) x = fmaf(rs[u], b2, x);
-          if (p.relu) x = fmaxf(x, 0.f);
-          if (p.mask) x = mk[u] > 0.f ? x : 0.f;
+          if (p.relu) x = relu_f(x);
+          if (p.mask) x = relu_bwd(mk[u], x);
           if (row0 + 8 * q + u >= p.M) continue;
           if (cbf) reinterpret_cast<uint16_t*>(p.C)[ci[u]] = bf_rne(x);
           else p.C[ci[u]] = x;

@@ -77,16 +77,36 @@ __device__ __forceinline__ void scale_pk(float (&acc)[VPL], float a) {
 __device__ __forceinline__ int pk_slot(int h, int i, int lane) {
   return (((h >> 1) * 2 + (i >> 1)) * 64 + lane) * 4 + (i & 1) * 2 + (h & 1);
 }
+// v where the lane's head mask m is all ones, +0 where it is 0: a bit select, so a non-finite v of
+// another head is dropped (a product with a 0/1 mask would make it NaN: 0 * inf)
+__device__ __forceinline__ float keep(float v, unsigned m) { return f_bits(u_bits(v) & m); }
+
+// The lane's head mask as a 0/1 factor: on finite values a product with it is the select, and it packs
+// into the fp32 pair math; non-finite values take the bit select (odd(), below).
+__device__ __forceinline__ float mkf(unsigned m) { return f_bits(m & 0x3f800000u); }
+// Wave-uniform: some lane holds a non-finite value in v (the sum times 0 is NaN exactly then).
+template <int N>
+__device__ __forceinline__ bool odd(const float (&v)[N]) {
+  float t = v[0];
+#pragma unroll
+  for (int i = 1; i < N; ++i) t += v[i];
+  t *= 0.f;
+  return __any(t != t);
+}
+
 // (dot4(v_h, f) , dot4(v_h+1, f)) for the head pair whose interleaved vectors start at `pair`,
-// then fmaf(mk, qk, .) per head
-__device__ __forceinline__ f2 dot4_pair(const float* pair, int lane, f4 f, f2 mk, float qk) {
+// then + qk for the lane's own head (masks mk0, mk1): SAFE by bit selects, else as a packed fma with
+// the 0/1 factors (the same bits on finite qk)
+template <bool SAFE>
+__device__ __forceinline__ f2 dot4_pair(const float* pair, int lane, f4 f, unsigned mk0, unsigned mk1, float qk) {
   const f4 A = *reinterpret_cast<const f4*>(pair + lane * 4);
   const f4 B = *reinterpret_cast<const f4*>(pair + (64 + lane) * 4);
   f2 acc = f2{A.x, A.y} * f2{f.x, f.x};
   acc = __builtin_elementwise_fma(f2{A.z, A.w}, f2{f.y, f.y}, acc);
   acc = __builtin_elementwise_fma(f2{B.x, B.y}, f2{f.z, f.z}, acc);
   acc = __builtin_elementwise_fma(f2{B.z, B.w}, f2{f.w, f.w}, acc);
-  return __builtin_elementwise_fma(mk, f2{qk, qk}, acc);
+  if constexpr (SAFE) return acc + f2{keep(qk, mk0), keep(qk, mk1)};
+  else return __builtin_elementwise_fma(f2{mkf(mk0), mkf(mk1)}, f2{qk, qk}, acc);
 }
 
 // bf16 storage (config C3, the reference's autocast: Linear outputs in bf16, train.py:632-636): the
@@ -165,7 +185,7 @@ __device__ __forceinline__ void angle_rows(const XRow& xr, const W1Regs& W, Edge
     float f[VPL];
 #pragma unroll
     for (int m = 0; m < VPL; ++m) {
-      f[m] = fmaxf(acc[m][j] + W.b[m], 0.f);
+      f[m] = relu_f(acc[m][j] + W.b[m]);
       if constexpr (BF) f[m] = (float)(__bf16)f[m];
     }
     e[j].f = f4{f[0], f[1], f[2], f[3]};
@@ -195,15 +215,19 @@ struct Params {
   DropParams drop;
 };
 
-// The group's four source ids.  One scalar load of src_at[t0..t0+3] when that lies inside the array:
-// entries past the segment's last edge are the next segment's sources — valid rows, and those edges
-// are masked out of the arithmetic.  Loading them one by one, clamped, compiled to four dependent
-// s_load / s_waitcnt round trips per group on the wave's critical path.
+// The group's four source ids.  One scalar load of src_at[t0..t0+3] when that lies inside the array;
+// entries past the segment's last edge (the next segment's sources) are replaced by the segment's own
+// last source with scalar selects: those rows carry a zero weight, and 0 * (a non-finite K or V row of
+// another target's source) would be NaN in this target.  Loading them one by one, clamped, compiled
+// to four dependent s_load / s_waitcnt round trips per group on the wave's critical path.
 typedef int i4u __attribute__((ext_vector_type(4), aligned(4)));
 __device__ __forceinline__ void group_src(const Params& p, int32_t t0, int32_t last, int32_t (&s)[G]) {
   if ((int64_t)t0 + G <= p.m) {
     const i4u v = *((const __attribute__((address_space(4))) i4u*)(p.src_at + t0));
-    s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
+    s[0] = v.x;
+    s[1] = t0 + 1 <= last ? v.y : s[0];
+    s[2] = t0 + 2 <= last ? v.z : s[1];
+    s[3] = t0 + 3 <= last ? v.w : s[2];
   } else {
 #pragma unroll
     for (int j = 0; j < G; ++j) s[j] = sld(p.src_at, min(t0 + j, last));
@@ -315,15 +339,23 @@ __device__ __forceinline__ float own(const float (&e)[H], int hl) {
   return pick_r<H>(e, hl);
 }
 
-// Lane's own-head entry of per-head wave-uniform values, as sum_h e[h] * mk[h] (mk = the lane's
-// one-hot head mask): exact for finite e (one product is e[hl] * 1, the others 0) and branch-free —
-// own() over uniform values compiled to one exec-masked branch per head inside the edge loop.
-template <int H>
-__device__ __forceinline__ float sel_head(const float (&e)[H], const float (&mk)[H]) {
-  float r = e[0] * mk[0];
+// Lane's own-head entry of per-head wave-uniform values, as OR_h (e[h] & mk[h]) (mk = the lane's
+// head masks: all ones for its own head, 0 for the others): the bits of e[hl] whatever the other
+// heads hold, and branch-free — own() over uniform values compiled to one exec-masked branch per
+// head inside the edge loop.
+template <int H, bool SAFE = true>
+__device__ __forceinline__ float sel_head(const float (&e)[H], const unsigned (&mk)[H]) {
+  if constexpr (SAFE) {
+    unsigned r = u_bits(e[0]) & mk[0];
 #pragma unroll
-  for (int h = 1; h < H; ++h) r = fmaf(e[h], mk[h], r);
-  return r;
+    for (int h = 1; h < H; ++h) r = (u_bits(e[h]) & mk[h]) | r;
+    return f_bits(r);
+  } else {   // finite e: sum_h e[h] * (0 or 1), exactly e[hl]
+    float r = e[0] * mkf(mk[0]);
+#pragma unroll
+    for (int h = 1; h < H; ++h) r = fmaf(e[h], mkf(mk[h]), r);
+    return r;
+  }
 }
 
 // Per-edge-head output rows [t, H] written by the first lanes of each 16-lane row.
@@ -399,10 +431,12 @@ struct Occ {
 // =============================================================================================
 // Forward: aggV = sum alpha' V_src, S[h] = sum alpha'_h f_t (normalised), sumA, mstat, den
 // =============================================================================================
-template <int H, int NR, bool DROP>
+// FAST: keep the packed 0/1-factor form for waves that see only finite values; off for the bf16-row
+// forward at four waves per SIMD, whose 128 registers have no room for both forms (it spilled).
+template <int H, int NR, bool DROP, bool FAST = true>
 __device__ __forceinline__ void fwd_group(const Params& p, const Edge (&r)[G], const float* uv, int32_t tb,
                                           int32_t end, int lane, int hl, int j0, float scale, const float (&q)[VPL],
-                                          const float (&mk)[H], const float (&c)[H], float (&m)[H],
+                                          const unsigned (&mk)[H], const float (&c)[H], float (&m)[H],
                                           float (&s_row)[H], float (&sa_row)[H], float (&accS)[H][VPL],
                                           float (&accV)[VPL]) {
   constexpr int RS = 64 * VPL;
@@ -414,22 +448,29 @@ __device__ __forceinline__ void fwd_group(const Params& p, const Edge (&r)[G], c
 #pragma unroll
     for (int j = 0; j < G; ++j) qk[j] = dot4(q, r[j].k);
     if constexpr (ALIGNN_LG3_PK && H % 2 == 0) {
+      auto scores = [&](auto safe) {
 #pragma unroll
-      for (int hp = 0; hp < H / 2; ++hp) {
+        for (int hp = 0; hp < H / 2; ++hp) {
 #pragma unroll
-        for (int j = 0; j < G; ++j) {
-          const f2 v = dot4_pair(uv + hp * 2 * RS, lane, r[j].f, f2{mk[2 * hp], mk[2 * hp + 1]}, qk[j]);
-          ps[j * H + 2 * hp] = v.x;
-          ps[j * H + 2 * hp + 1] = v.y;
+          for (int j = 0; j < G; ++j) {
+            const f2 v = dot4_pair<decltype(safe)::value>(uv + hp * 2 * RS, lane, r[j].f, mk[2 * hp], mk[2 * hp + 1],
+                                                          qk[j]);
+            ps[j * H + 2 * hp] = v.x;
+            ps[j * H + 2 * hp + 1] = v.y;
+          }
         }
-      }
+      };
+      // wave-uniform: the 0/1-factor form unless some q.k partial is non-finite (0 * inf would reach
+      // the other heads)
+      if (!FAST || odd(qk)) scores(std::true_type{});
+      else scores(std::false_type{});
     } else {
 #pragma unroll
       for (int h = 0; h < H; ++h) {
         float u[VPL];
         vload(uv + h * RS + j0, u);
 #pragma unroll
-        for (int j = 0; j < G; ++j) ps[j * H + h] = fmaf(mk[h], qk[j], dot4(u, r[j].f));
+        for (int j = 0; j < G; ++j) ps[j * H + h] = keep(qk[j], mk[h]) + dot4(u, r[j].f);
       }
     }
     reduce_rows<G * H>(ps, b);  // row j: b[h] = score partial of (edge tb + j, head h)
@@ -489,27 +530,31 @@ __device__ __forceinline__ void fwd_group(const Params& p, const Edge (&r)[G], c
     ed[h] = ex * mul[h];
     sa_row[h] += ed[h];
   }
+  auto accumulate = [&](auto safe) {
 #pragma unroll
-  for (int j = 0; j < G; ++j) {
-    float e[H];
+    for (int j = 0; j < G; ++j) {
+      float e[H];
 #pragma unroll
-    for (int h = 0; h < H; ++h) {
-      e[h] = readlane_f(ed[h], 16 * j);
+      for (int h = 0; h < H; ++h) {
+        e[h] = readlane_f(ed[h], 16 * j);
+        if constexpr (ALIGNN_LG3_PK) {
+          axpy_pk(accS[h], e[h], r[j].f);
+        } else {
+#pragma unroll
+          for (int i = 0; i < VPL; ++i) accS[h][i] = fmaf(e[h], r[j].f[i], accS[h][i]);
+        }
+      }
+      const float el = ALIGNN_LG3_PK ? sel_head<H, decltype(safe)::value>(e, mk) : own<H>(e, hl);
       if constexpr (ALIGNN_LG3_PK) {
-        axpy_pk(accS[h], e[h], r[j].f);
+        axpy_pk(accV, el, r[j].v);
       } else {
 #pragma unroll
-        for (int i = 0; i < VPL; ++i) accS[h][i] = fmaf(e[h], r[j].f[i], accS[h][i]);
+        for (int i = 0; i < VPL; ++i) accV[i] = fmaf(el, r[j].v[i], accV[i]);
       }
     }
-    const float el = ALIGNN_LG3_PK ? sel_head<H>(e, mk) : own<H>(e, hl);
-    if constexpr (ALIGNN_LG3_PK) {
-      axpy_pk(accV, el, r[j].v);
-    } else {
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) accV[i] = fmaf(el, r[j].v[i], accV[i]);
-    }
-  }
+  };
+  if (!FAST || odd(ed)) accumulate(std::true_type{});   // wave-uniform, as for the scores
+  else accumulate(std::false_type{});
 }
 
 template <int H, int NR, bool DROP, bool BF, bool XF>
@@ -527,9 +572,9 @@ void lg3_fwd_kernel(Params p) {
   const int64_t d = (int64_t)uni(sld(p.items, (int64_t)blockIdx.x));
   const int32_t beg = uni(sld(p.off, d)), end = uni(sld(p.off, d + 1));
 
-  float mk[H];
+  unsigned mk[H];
 #pragma unroll
-  for (int h = 0; h < H; ++h) mk[h] = (h == hl) ? 1.0f : 0.0f;
+  for (int h = 0; h < H; ++h) mk[h] = (h == hl) ? 0xffffffffu : 0u;
   float accS[H][VPL], accV[VPL], m[H], s_row[H], sa_row[H];
 #pragma unroll
   for (int h = 0; h < H; ++h) {
@@ -578,7 +623,8 @@ void lg3_fwd_kernel(Params p) {
       Edge e[G];
       to_f32<BF, XF>(r, e);
       if constexpr (XF) angle_rows<BF>(xr, W, e);
-      fwd_group<H, NR, DROP>(p, e, uv, t, end, lane, hl, j0, scale, q, mk, c, m, s_row, sa_row, accS, accV);
+      fwd_group<H, NR, DROP, !(BF && NR == 1 && !XF)>(p, e, uv, t, end, lane, hl, j0, scale, q, mk, c, m, s_row, sa_row,
+                                                      accS, accV);
     };
     if constexpr (NR == 1) {
       for (int32_t tb = beg;; tb += G) {
@@ -640,7 +686,7 @@ void lg3_fwd_kernel(Params p) {
 template <int H, int NR, bool DROP>
 __device__ __forceinline__ void bwd_group(const Params& p, const Edge (&r)[G], const float* uv, int32_t tb,
                                           int32_t end, int lane, int hl, int j0, float scale,
-                                          const float (&q)[VPL], const float (&go)[VPL], const float (&mk)[H],
+                                          const float (&q)[VPL], const float (&go)[VPL], const unsigned (&mk)[H],
                                           const float (&c)[3 * H], const float (&mst)[H],
                                           const float (&inv_den)[H], float (&sgz_row)[H], float (&sz)[H][VPL],
                                           float (&dqa)[VPL]) {
@@ -657,19 +703,24 @@ __device__ __forceinline__ void bwd_group(const Params& p, const Edge (&r)[G], c
       gv[j] = dot4(go, r[j].v);
     }
     if constexpr (ALIGNN_LG3_PK && H % 2 == 0) {
+      auto scores = [&](auto safe) {
+        constexpr bool S = decltype(safe)::value;
 #pragma unroll
-      for (int hp = 0; hp < H / 2; ++hp) {
-        const f2 mk2 = {mk[2 * hp], mk[2 * hp + 1]};
+        for (int hp = 0; hp < H / 2; ++hp) {
 #pragma unroll
-        for (int j = 0; j < G; ++j) {
-          const f2 a = dot4_pair(uv + hp * 2 * RS, lane, r[j].f, mk2, qk[j]);
-          const f2 b = dot4_pair(uv + (H + 2 * hp) * RS, lane, r[j].f, mk2, gv[j]);
-          ps[j * H + 2 * hp] = a.x;
-          ps[j * H + 2 * hp + 1] = a.y;
-          pd[j * H + 2 * hp] = b.x;
-          pd[j * H + 2 * hp + 1] = b.y;
+          for (int j = 0; j < G; ++j) {
+            const f2 a = dot4_pair<S>(uv + hp * 2 * RS, lane, r[j].f, mk[2 * hp], mk[2 * hp + 1], qk[j]);
+            const f2 b = dot4_pair<S>(uv + (H + 2 * hp) * RS, lane, r[j].f, mk[2 * hp], mk[2 * hp + 1], gv[j]);
+            ps[j * H + 2 * hp] = a.x;
+            ps[j * H + 2 * hp + 1] = a.y;
+            pd[j * H + 2 * hp] = b.x;
+            pd[j * H + 2 * hp + 1] = b.y;
+          }
         }
-      }
+      };
+      const float qg[2 * G] = {qk[0], qk[1], qk[2], qk[3], gv[0], gv[1], gv[2], gv[3]};
+      if (odd(qg)) scores(std::true_type{});   // wave-uniform (fwd_group)
+      else scores(std::false_type{});
     } else {
 #pragma unroll
       for (int h = 0; h < H; ++h) {
@@ -678,8 +729,8 @@ __device__ __forceinline__ void bwd_group(const Params& p, const Edge (&r)[G], c
         vload(uv + (H + h) * RS + j0, vd);
 #pragma unroll
         for (int j = 0; j < G; ++j) {
-          ps[j * H + h] = fmaf(mk[h], qk[j], dot4(u, r[j].f));
-          pd[j * H + h] = fmaf(mk[h], gv[j], dot4(vd, r[j].f));
+          ps[j * H + h] = keep(qk[j], mk[h]) + dot4(u, r[j].f);
+          pd[j * H + h] = keep(gv[j], mk[h]) + dot4(vd, r[j].f);
         }
       }
     }
@@ -709,27 +760,31 @@ __device__ __forceinline__ void bwd_group(const Params& p, const Edge (&r)[G], c
       store_edge_heads<H>(p.alpha_e, t, col, bd);
     }
   }
+  auto accumulate = [&](auto safe) {
 #pragma unroll
-  for (int j = 0; j < G; ++j) {
-    float e[H];
+    for (int j = 0; j < G; ++j) {
+      float e[H];
 #pragma unroll
-    for (int h = 0; h < H; ++h) {
-      e[h] = readlane_f(bs[h], 16 * j);
+      for (int h = 0; h < H; ++h) {
+        e[h] = readlane_f(bs[h], 16 * j);
+        if constexpr (ALIGNN_LG3_PK) {
+          axpy_pk(sz[h], e[h], r[j].f);
+        } else {
+#pragma unroll
+          for (int i = 0; i < VPL; ++i) sz[h][i] = fmaf(e[h], r[j].f[i], sz[h][i]);
+        }
+      }
+      const float dzl = ALIGNN_LG3_PK ? sel_head<H, decltype(safe)::value>(e, mk) : own<H>(e, hl);
       if constexpr (ALIGNN_LG3_PK) {
-        axpy_pk(sz[h], e[h], r[j].f);
+        axpy_pk(dqa, dzl, r[j].k);
       } else {
 #pragma unroll
-        for (int i = 0; i < VPL; ++i) sz[h][i] = fmaf(e[h], r[j].f[i], sz[h][i]);
+        for (int i = 0; i < VPL; ++i) dqa[i] = fmaf(dzl, r[j].k[i], dqa[i]);
       }
     }
-    const float dzl = ALIGNN_LG3_PK ? sel_head<H>(e, mk) : own<H>(e, hl);
-    if constexpr (ALIGNN_LG3_PK) {
-      axpy_pk(dqa, dzl, r[j].k);
-    } else {
-#pragma unroll
-      for (int i = 0; i < VPL; ++i) dqa[i] = fmaf(dzl, r[j].k[i], dqa[i]);
-    }
-  }
+  };
+  if (odd(bs)) accumulate(std::true_type{});   // wave-uniform (fwd_group)
+  else accumulate(std::false_type{});
 }
 
 template <int H, int NR, bool DROP, bool BF, bool XF>
@@ -747,9 +802,9 @@ void lg3_bwd_dst_kernel(Params p) {
   const int64_t d = (int64_t)uni(sld(p.items, (int64_t)blockIdx.x));
   const int32_t beg = uni(sld(p.off, d)), end = uni(sld(p.off, d + 1));
 
-  float mk[H];
+  unsigned mk[H];
 #pragma unroll
-  for (int h = 0; h < H; ++h) mk[h] = (h == hl) ? 1.0f : 0.0f;
+  for (int h = 0; h < H; ++h) mk[h] = (h == hl) ? 0xffffffffu : 0u;
   float sz[H][VPL], sgz_row[H], dqa[VPL];
 #pragma unroll
   for (int h = 0; h < H; ++h) {

@@ -75,13 +75,13 @@ __device__ __forceinline__ bf8 pack8(const f4& a, const f4& b) {
   v[4] = (__bf16)b[0]; v[5] = (__bf16)b[1]; v[6] = (__bf16)b[2]; v[7] = (__bf16)b[3];
   return v;
 }
-// relu(bf16(a | b)): autocast's order (the Linear's bf16 output, then ReLU), on the rounded bits — a
-// bf16 orders as its int16 bits do on either side of zero, so one v_pk_max_i16 per two elements
+// relu(bf16(a | b)): autocast's order (the Linear's bf16 output, then ReLU), on the rounded values.
+// Per element (common.h relu_bf), not a packed int16 max against 0: that would zero a negative-sign NaN.
 __device__ __forceinline__ bf8 relu_pack8(const f4& a, const f4& b) {
-  u4 v = __builtin_bit_cast(u4, pack8(a, b));
+  bf8 v = pack8(a, b);
 #pragma unroll
-  for (int i = 0; i < 4; ++i) asm("v_pk_max_i16 %0, %1, 0" : "=v"(v[i]) : "v"(v[i]));
-  return __builtin_bit_cast(bf8, v);
+  for (int i = 0; i < 8; ++i) v[i] = relu_bf(v[i]);
+  return v;
 }
 // v = hi + lo with hi = bf16(v), lo = bf16(v - hi): the A operand of an aggregation as two fragments
 __device__ __forceinline__ void split8(const f4& a, const f4& b, bf8& hi, bf8& lo) {
@@ -337,10 +337,12 @@ __device__ __forceinline__ void fwd_pair(const Params& p, const PairIn& in, int3
     for (int t = 0; t < 4; ++t) T[t] = mma(W1f.get(t, lane), in.X[x], zero4());
     f4 Zp = mma(relu_pack8(T[0], T[1]), Uf[0], zero4());
     Zp = mma(relu_pack8(T[2], T[3]), Uf[1], Zp);
-    Zp = mma(in.G[x][0], Qf[0], Zp);
-    Zp = mma(in.G[x][1], Qf[1], Zp);
+    // Q.K in an accumulator of its own, taken by the wave's own head only (a select): Qf is zero in the
+    // other heads' columns, and 0 * (a non-finite K element) would make their scores NaN
+    f4 Zq = mma(in.G[x][0], Qf[0], zero4());
+    Zq = mma(in.G[x][1], Qf[1], Zq);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) Zp[r] += cadd;
+    for (int r = 0; r < 4; ++r) Zp[r] = (Zp[r] + (hc == w ? Zq[r] : 0.f)) + cadd;
     if (c < H) *reinterpret_cast<f4*>(&zb[buf][w][x][c][4 * g]) = Zp;
   }
   bf8 FB[4];
@@ -589,16 +591,17 @@ __device__ __forceinline__ void bwd_pair(const Params& p, const PairIn& in, int3
     const bf8 K0 = row_frag(img, x, 0, g, c), K1 = row_frag(img, x, 1, g, c);
     f4 Zp = mma(F0, k.Uf[0], zero4());
     Zp = mma(F1, k.Uf[1], Zp);
-    Zp = mma(K0, k.Qf[0], Zp);
-    Zp = mma(K1, k.Qf[1], Zp);
     f4 Yp = mma(F0, k.Vf[0], zero4());
     Yp = mma(F1, k.Vf[1], Yp);
-    Yp = mma(in.G[x][0], k.Of[0], Yp);
-    Yp = mma(in.G[x][1], k.Of[1], Yp);
+    // Q.K and dout.V for the wave's own head only, by a select (fwd_pair)
+    f4 Zq = mma(K0, k.Qf[0], zero4());
+    Zq = mma(K1, k.Qf[1], Zq);
+    f4 Yq = mma(in.G[x][0], k.Of[0], zero4());
+    Yq = mma(in.G[x][1], k.Of[1], Yq);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      Zp[r] += k.zadd;
-      Yp[r] += k.yadd;
+      Zp[r] = (Zp[r] + (hc == w ? Zq[r] : 0.f)) + k.zadd;
+      Yp[r] = (Yp[r] + (hc == w ? Yq[r] : 0.f)) + k.yadd;
     }
     if (c < H) {
       *reinterpret_cast<f4*>(&zb[buf][w][0][x][c][4 * g]) = Zp;

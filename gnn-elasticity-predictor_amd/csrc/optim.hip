@@ -135,7 +135,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   const float ss0 = (float)(lr0 / bc1), ss1 = (float)(lr1 / bc1);
   const float dec0 = (float)(1.0 - lr0 * wd), dec1 = (float)(1.0 - lr1 * wd);
   float c = 1.0f;
-  if (norm) c = fminf(max_norm / (*norm + 1e-6f), 1.0f);
+  if (norm) c = clamp_max(max_norm / (*norm + 1e-6f), 1.0f);   // a NaN norm gives a NaN coefficient
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const bool g0 = i < split;
     const float gi = g[i] * c;

@@ -108,7 +108,7 @@ __global__ __launch_bounds__(256) void gate_ln_fwd_kernel(GateFwdParams p) {
     float out[VPL];
 #pragma unroll
     for (int i = 0; i < VPL; ++i) {
-      float a = fmaxf((y[i] - mean) * rs * g[i] + bb[i], 0.f);
+      float a = relu_f((y[i] - mean) * rs * g[i] + bb[i]);
       if (p.drop.active) a *= dropout_mul(p.drop.seed, (uint64_t)row * D + j0 + i, p.drop.thresh, p.drop.inv_keep);
       out[i] = x[i] + a;
     }
@@ -248,7 +248,7 @@ __global__ __launch_bounds__(256) void gate_ln_bwd_kernel(GateBwdParams p) {
       float ga = gx[i];
       if (p.drop.active && act)
         ga *= dropout_mul(p.drop.seed, (uint64_t)row * D + j0 + i, p.drop.thresh, p.drop.inv_keep);
-      const float gl = (act && ln > 0.f) ? ga : 0.f;
+      const float gl = (act && relu_on(ln)) ? ga : 0.f;
       a_g[i] = fmaf(gl, yh[i], a_g[i]);
       a_b[i] += gl;
       gyh[i] = gl * g[i];
@@ -418,7 +418,7 @@ __global__ void dropout_kernel(int64_t rows, int64_t cols, const float* __restri
     const int64_t r = i / cols, c = i % cols;
     float v = x[r * ldx + c];
     if (drop.active) v *= dropout_mul(drop.seed, (uint64_t)i, drop.thresh, drop.inv_keep);
-    if (ref) v = ref[r * ldr + c] > 0.f ? v : 0.f;
+    if (ref) v = relu_bwd(ref[r * ldr + c], v);
     y[r * ldy + c] = v;
   }
 }
@@ -438,14 +438,17 @@ __global__ __launch_bounds__(256) void hetero_nll_kernel(int64_t B, int T, const
     const int t = (int)(i % T);
     const float mu = heads[b * ldh + t];
     const float lvr = heads[b * ldh + T + t];
-    const float lv = fmaxf(lvr, floor);
+    const float lv = clamp_min(lvr, floor);
     const float yz = (logf(y[b * T + t]) - lm[t]) / ls[t];
     const float var = expf(lv);
     const float diff = mu - yz;
     const float wb = w ? w[b] : 1.0f;  // KNN sample weight (train.py:660-674): scales the NLL term only
     acc += wb * (0.5f * (lv + diff * diff / var)) + l2 * (0.5f * lv) * (0.5f * lv);
     dh[b * lddh + t] = inv * wb * diff / var;
-    const float dlv = inv * (wb * 0.5f * (1.0f - diff * diff / var) + l2 * 0.5f * lv);
+    // autograd reaches lv through var = exp(lv) as -(diff^2 / var^2) * var, which at lv = +inf is
+    // 0 * inf = NaN, not the limit 0 (finite var: q itself, the same bits)
+    const float q = diff * diff / var;
+    const float dlv = inv * (wb * 0.5f * (1.0f - (__builtin_isinf(var) ? q * var : q)) + l2 * 0.5f * lv);
     dh[b * lddh + T + t] = lvr >= floor ? dlv : 0.f;
   }
   red[threadIdx.x] = acc;
@@ -484,7 +487,7 @@ __global__ __launch_bounds__(256) void hetero_nll_amp_kernel(int64_t B, int T, c
     const int t = (int)(i % T);
     const float mu = bf16r(heads[b * ldh + t]);
     const float lvr = bf16r(heads[b * ldh + T + t]);
-    const float lc = (lvr != lvr) ? lvr : fmaxf(lvr, floor16);
+    const float lc = clamp_min(lvr, floor16);
     const float yt = bf16r((logf(y[b * T + t]) - lm[t]) / ls[t]);
     const float d = bf16r(mu - yt);
     const float p = d * d;

@@ -62,7 +62,7 @@ __global__ __launch_bounds__(256) void linear_smallk_kernel(const float* __restr
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         a[j] += b[j];
-        if (relu) a[j] = fmaxf(a[j], 0.f);
+        if (relu) a[j] = relu_f(a[j]);
       }
       if constexpr (sizeof(OutT) == 4) {
         *reinterpret_cast<float4*>(out + (r0 + r) * ldo + c0) = make_float4(a[0], a[1], a[2], a[3]);
@@ -272,7 +272,7 @@ __global__ __launch_bounds__(256) void linear_smallk_bf16_mx_kernel(const float*
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const __bf16 b = (__bf16)pre[4 * q + i];
-            h[i] = (relu && !((float)b > 0.f)) ? (__bf16)0.f : b;
+            h[i] = relu ? relu_bf(b) : b;
           }
           *reinterpret_cast<skh4*>(img + r * SKM_LDT + 32 * tl + 8 * q + 4 * hh) = h;
         }

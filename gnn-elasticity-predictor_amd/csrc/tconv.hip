@@ -627,7 +627,7 @@ __device__ __forceinline__ void bwd2_node(const BwdDstParams& p, float* smem, in
           }
           if (tb + j < end && act) {
 #pragma unroll
-            for (int i = 0; i < VPL; ++i) df[i] = (p.acc_dF & 2) ? (f[j][i] > 0.f ? df[i] : 0.f) : df[i];
+            for (int i = 0; i < VPL; ++i) df[i] = (p.acc_dF & 2) ? relu_bwd(f[j][i], df[i]) : df[i];
             if (p.dfbf) vstore_bf(reinterpret_cast<uint16_t*>(p.dF) + rw[j] * p.lddf + j0, df);
             else vstore(p.dF + rw[j] * p.lddf + j0, df);
           }

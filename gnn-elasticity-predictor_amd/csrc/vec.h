@@ -2,7 +2,21 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "common.h"
+
 namespace alignn {
+
+// Packed forms of common.h's relu_f / relu_bwd, per component (a packed max alone drops NaN).
+// ReLU of a four-float ext-vector:
+template <typename V4>
+__device__ __forceinline__ V4 relu4(const V4& v) {
+  return V4{relu_f(v.x), relu_f(v.y), relu_f(v.z), relu_f(v.w)};
+}
+// ReLU backward of four values from four forward results:
+template <typename V4>
+__device__ __forceinline__ V4 relu_bwd4(const V4& result, const V4& g) {
+  return V4{relu_bwd(result.x, g.x), relu_bwd(result.y, g.y), relu_bwd(result.z, g.z), relu_bwd(result.w, g.w)};
+}
 
 template <int VPL>
 __device__ __forceinline__ void vload(const float* __restrict__ p, float (&v)[VPL]) {
