@@ -7,6 +7,7 @@ Public API mirrors the reference: ``EdgeUpdateBlock``, ``NodeUpdateBlock``, ``Al
 fused per-batch training step).  Compute runs in ``libalignn_hip.so`` (HIP, gfx950).
 """
 from .data import Batch, Data, DataLoader  # noqa: F401
+from .evaluate import EvalMetrics, eval_epoch_hetero  # noqa: F401
 from .layout import AlignnConfig  # noqa: F401
 from .model import (AlignnRegressor, EdgeUpdateBlock, HeteroAlignnRegressor, NodeUpdateBlock,  # noqa: F401
                     TransformerConv)

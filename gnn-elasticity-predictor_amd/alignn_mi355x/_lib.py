@@ -137,6 +137,10 @@ _SIGNATURES = {
     "alignn_ensemble_moments": ([c_i32, c_i64, c_i32, c_vp, c_i64, c_i64, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, c_vp, c_vp], c_i32),
     "alignn_member_mean_f32": ([c_i32, c_i64, c_vp, c_i64, c_vp, c_vp], c_i32),
+    "alignn_eval_accumulate": ([c_i64, c_i32, c_vp, c_i32, c_i64, c_vp, c_vp, c_vp, c_f32, c_vp, c_vp, c_i32, c_vp,
+                                c_vp, c_vp, c_i64, c_vp], c_i32),
+    "alignn_eval_spearman": ([c_i64, c_vp, c_vp, c_vp, c_vp, c_vp], c_i32),
+    "alignn_eval_finalize": ([c_vp, c_i64, c_vp, c_i32, c_vp, c_vp], c_i32),
     "alignn_grad_norm_f32": ([c_vp, c_i64, c_vp, c_vp, c_vp], c_i32),
     "alignn_collate_rows_f32": ([c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp], c_i32),
     "alignn_collate_index_i64": ([c_i32, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp], c_i32),

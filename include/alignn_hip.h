@@ -548,6 +548,65 @@ int alignn_ensemble_moments(int32_t M, int64_t B, int32_t T, const float* heads,
 int alignn_member_mean_f32(int32_t M, int64_t n, const float* x, int64_t member_stride, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Validation epoch on the device: eval_epoch_hetero's nine metrics (train.py:726-846) without a
+ * host read per batch.  One small state block of doubles lives on the device for the epoch; every
+ * entry but sigma_max and the cursor is a plain sum (counts in doubles are exact).
+ * ---------------------------------------------------------------------------------------- */
+#define ALIGNN_EVAL_STATE_DOUBLES 16
+#define ALIGNN_EVAL_S_LOSS 0       /* sum over graphs of the mean NLL over targets */
+#define ALIGNN_EVAL_S_GRAPHS 1
+#define ALIGNN_EVAL_S_LV_SUM 2     /* clamped log-variance */
+#define ALIGNN_EVAL_S_LV_COUNT 3
+#define ALIGNN_EVAL_S_SIGMA_MAX 4  /* starts at -inf */
+#define ALIGNN_EVAL_S_COV_HITS 5   /* |y_z - mean| <= sigma */
+#define ALIGNN_EVAL_S_ELEMS 6
+#define ALIGNN_EVAL_S_ECE_SUM 7    /* per batch: sum over levels of |coverage_l - p_l| */
+#define ALIGNN_EVAL_S_ECE_TERMS 8  /* += levels per batch */
+#define ALIGNN_EVAL_S_ABS 9        /* linear absolute error */
+#define ALIGNN_EVAL_S_SQ 10        /* linear squared error */
+#define ALIGNN_EVAL_S_LOGABS 11    /* log absolute error */
+#define ALIGNN_EVAL_S_BAD 12       /* targets <= 0 under a transformer */
+#define ALIGNN_EVAL_S_CURSOR 13    /* write cursor of the two epoch buffers */
+#define ALIGNN_EVAL_S_SPEARMAN 14  /* free for the caller: the Python side keeps Spearman's output here */
+#define ALIGNN_EVAL_LEVELS 9
+#define ALIGNN_EVAL_OUT_DOUBLES 10
+#define ALIGNN_EVAL_RANK_TILE 1024
+#define ALIGNN_EVAL_SPEARMAN_MAX_N 4194304
+
+/* One batch into the state (one launch, one workgroup, fixed-order reduction, no atomics).
+ *   heads [B, ldh]: mean at col 0..T-1, logvar at T..2T-1; fp32, or bf16 (heads_bf16 != 0) widened to
+ *   fp32 before any arithmetic.  y [B, T] raw targets.  log_means/log_stds [T] or both NULL (no
+ *   transformer: the target is used as is).  z_thresholds/prob_levels [9] on the device.
+ *   Per element lv = max(logvar, floor), sigma = sqrt(exp(lv)), y_z = (log y - m)/s, d = mean - y_z,
+ *   nll = 0.5(lv + d^2/exp(lv)), pred = exp(mean*s + m); linear abs/squared error of pred against y,
+ *   log abs error of log(max(pred, 1e-6)) against log(max(y, 1e-6)) when compute_log_mae.
+ *   ECE keeps the reference's per-batch shape (train.py:803-807); the batch's sigma maximum keeps a
+ *   NaN and the merge into the epoch's drops it (train.py:782).  |d| and max(sigma, 1e-6) go to
+ *   err_buf/sig_buf [capacity] at the state's cursor (elements past capacity are not written), and
+ *   the cursor advances by B*T.  A target <= 0 under a transformer adds to S_BAD and to no sum; its
+ *   buffer slots hold NaN.  B == 0 is a no-op.  For a padded batch pass the real rows only. */
+int alignn_eval_accumulate(int64_t B, int32_t T, const void* heads, int32_t heads_bf16, int64_t ldh,
+                           const float* y, const float* log_means, const float* log_stds,
+                           float min_logvar_floor, const float* z_thresholds, const float* prob_levels,
+                           int32_t compute_log_mae, double* state, float* err_buf, float* sig_buf,
+                           int64_t capacity, void* stream);
+
+/* *out = Spearman correlation of err[0..n) and sig[0..n) over the pairs where both are finite,
+ * average ranks by counting (rank_i = #(x_j < x_i) + (#(x_j == x_i) + 1)/2: O(n^2), tie-exact,
+ * deterministic), Pearson of the ranks in double.  Fewer than two finite pairs or a constant rank
+ * vector: NaN.  workspace: 2 + 3n doubles; on return [0] = number of finite pairs m, [2, 2+m) the
+ * ranks of err and [2+n, 2+n+m) the ranks of sig, in the compacted order.
+ * n <= ALIGNN_EVAL_SPEARMAN_MAX_N. */
+int alignn_eval_spearman(int64_t n, const float* err, const float* sig, double* out, double* workspace,
+                         void* stream);
+
+/* out[0..9) = avg_loss, mae_linear, mae_log, rmse_linear, spearman, mean_log_variance, sigma_max,
+ * coverage, ece with the reference's denominators (both MAEs by dataset_size, train.py:827-828) and
+ * empty-epoch values (train.py:823-845); out[9] = S_BAD.  spearman: device double, NULL = NaN. */
+int alignn_eval_finalize(const double* state, int64_t dataset_size, const double* spearman,
+                         int32_t compute_log_mae, double* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Optimizer step over the flat buffers: clip_grad_norm_(5.0) + fused AdamW with
  * the reference's two param groups (train.py:693-699, :1516-1542).
  * alignn_grad_norm_f32: *norm = ||g||_2 (fixed-order two-stage sum; workspace >= 1024 floats).
